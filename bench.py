@@ -15,7 +15,13 @@ noise, seed 1000 + global trajectory index. 
 default (--batch trajectories per GPU); --global-batch G fixes the total instead (strong scaling:
 rank r owns shard_bounds(G, r, N)).
 
-The JSON line also carries `configs`: one measured record per BASELINE config.  On any number of
+A plain run measures the headline only: set-up, warm-up, exactly --steps timed steps, the line (`ms_per_step` = one timed
+step).  --dump-outputs DIR also writes what the last timed step computed (objectives, F, G; whole or a fixed seeded sample,
+at most 56 MB) as DIR/<name>.npy; the inputs depend on the arguments alone, so two builds can be compared output for output.
+Everything else below -- configs, CPU baseline, side records, the native C++ leg, the box calibration and the instrumented
+pass -- runs under --full.
+
+Under --full the JSON line also carries `configs`: one measured record per BASELINE config.  On any number of
 GPUs: configs[3] (global batch 1024, S10) and configs[4] (global batch 8192 mixed, fp64 and fp32) AS
 STATED, i.e. strong scaling -- every rank evaluates its shard and the objectives are all-gathered,
 inside the same process group after the headline.  On one GPU also the single-trajectory configs
@@ -28,7 +34,7 @@ for N > 1, directly as `python -m torch.distributed.run --nnodes=1 --nproc-per-n
 --master-port P bench.py --gpus N --steps K --warmup W`.  Rank 0 prints ONE JSON line.
 
 Every timed region is preceded by at least --warmup steps AND at least 0.25 s of back-to-back launching (a fresh box
-ramps its clocks over the first milliseconds; `warmup_steps_run` says how many steps that took), and followed by a
+ramps its clocks over the first milliseconds; `warmup_steps_run` says how many steps that took), and (--full) followed by a
 calibration of the box in the same process: the vendor's fill kernel and the bare store loop of the launch's own
 shape (`roofline.box_fill_GBs`, `box_stream_shape_GBs`, `frac_of_box_fill`, `vs_bare_store_loop`), so that a
 slow box can be told from a slow kernel.  Both are reference points measured beside the evaluation, not ceilings: the
@@ -386,12 +392,25 @@ class Job:
         return [float(v) for v in t]
 
 
+def output_sample(torch, a, rows, cols, budget, seed):
+    """The [rows][cols] part of the device array `a` (2-D) as a host array: whole when it fits in `budget` bytes, else a fixed
+    sample of budget / itemsize elements at sorted flat indices drawn from `seed` (the same for the same shape in every run)."""
+    n, k = rows * cols, budget // a.element_size()
+    v = a[:rows, :cols]
+    if n <= k:
+        return v.cpu().numpy()
+    idx = torch.from_numpy(np.unique(np.random.default_rng(seed).integers(0, n, k))).to(a.device)
+    return v[idx // cols, idx % cols].cpu().numpy()
+
+
 def sharded_run(tol_amd, job, mission, aircraft, ts, dtype, pattern, per_gpu, global_batch, steps, warmup, x_buffers, instrumented=True,
-                keep=None):
+                keep=None, outputs=None):
     """Exactly `steps` steps of one workload over the job's ranks between two barriers.  A step = this rank's shard in ONE
     launch (F, G and the objectives) + the all-gather of the objectives (N > 1; asynchronous, four buffers in rotation, so it
     overlaps the next step's launch).  per_gpu > 0: weak scaling, that many trajectories per rank; else global_batch
-    trajectories split by shard_bounds (strong scaling).  Returns the timings as maxima over the ranks."""
+    trajectories split by shard_bounds (strong scaling).  Returns the timings as maxima over the ranks.
+    outputs (a dict): filled with what the last timed step computed, as host arrays (output_sample): the objectives (all ranks',
+    in global trajectory order, when they are gathered) and this rank's F and G."""
     from tol_amd.distributed import shard_bounds
     torch, dist, world, rank = job.torch, job.dist, job.world, job.rank
     coll = job.collective
@@ -469,6 +488,18 @@ def sharded_run(tol_amd, job, mission, aircraft, ts, dtype, pattern, per_gpu, gl
     if coll:      # every rank's shard arrived in place, in global trajectory order
         mine = obj[last].to(allobj[last].device)
         assert torch.equal(allobj[last][rank * Bmax:(rank + 1) * Bmax], mine), "gathered objectives are out of order"
+    if outputs is not None:
+        # taken before the instrumented pass and the calibration below (the bare store loop leaves garbage in G); the budgets keep
+        # the three files under 64 MB together
+        if coll:
+            widths = [B] * world if per_gpu > 0 else [hi - lo for lo, hi in (shard_bounds(total, r, world) for r in range(world))]
+            objs = torch.cat([allobj[last][r * Bmax:r * Bmax + w] for r, w in enumerate(widths)])
+        else:
+            objs = obj[last][:B]
+        outputs["objectives"] = output_sample(torch, objs.view(-1, 1), objs.numel(), 1, 8 << 20, 1).reshape(-1)
+        if B > 0:
+            outputs["F"] = output_sample(torch, dF, B, bt.neF, 16 << 20, 2)
+            outputs["G"] = output_sample(torch, dG, B, bt.neG, 32 << 20, 3)
     out = {"B": B, "total": total, "scaling": scaling, "x_buffers": len(dXs), "buffers_reused": reused,
            "placement": getattr(bt, "placement", None)}
     # the gather alone (N > 1): synchronous all-gathers of the same buffers, nothing else in flight
@@ -506,7 +537,7 @@ def sharded_run(tol_amd, job, mission, aircraft, ts, dtype, pattern, per_gpu, gl
     # Calibration of THIS box in THIS process, right after the timed region (same clocks, same temperature): the vendor's
     # fill kernel, and the bare store loop of this launch's own shape on the same buffers (rank 0's figures are reported)
     out["box_fill_GBs"] = box_fill(torch, dF.device)
-    if B > 8:
+    if B > 8 and CALIBRATE:
         out["box_stream_shape_GBs"], out["box_stream_shape_us"] = store_shape_rate(bt, torch, dXs, dF, dG, B, ts, 46 if pattern == "compact" else 104)
     job.barrier()
     if keep is None:
@@ -795,7 +826,7 @@ def run_native_child(n, args, issue="grouped", timeout=420):
     """Start `bench.py --native-multi n` as a CHILD process (never an exec: this process has initialised the GPU) and return its
     record, or a record that says why there is none."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--native-multi", str(n), "--native-issue", issue, "--steps", str(args.steps),
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--native-multi", str(n), "--native-issue", issue, "--steps", str(args.steps),
            "--warmup", str(args.warmup), "--batch", str(args.batch), "--ts", str(args.ts), "--mission", args.mission,
            "--aircraft", args.aircraft, "--dtype", args.dtype, "--x-buffers", str(args.x_buffers), "--min-warm-seconds", str(MIN_WARM_S)]
     if args.global_batch > 0:
@@ -913,7 +944,16 @@ def main():
     ap.add_argument("--native-issue", default="grouped", choices=["grouped", "threads"],
                     help="how the native leg issues the all-gather: one ncclGroupStart/End bracket | one call per device thread")
     ap.add_argument("--no-native-multi", action="store_true", help="skip the native C++ leg")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the CPU baseline, the per-BASELINE-config records and side runs, the native "
+                         "C++ leg, the box calibration and the instrumented pass (the --no-* switches still leave parts out). "
+                         "Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy: objectives, F, G (rank 0's shard), each whole or "
+                         "as a fixed seeded sample, in the batch's dtype")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_configs = args.no_native_multi = args.no_calibration = True
 
     MIN_WARM_S, CALIBRATE = max(args.min_warm_seconds, 0.0), not args.no_calibration
     if args.native_multi > 0:
@@ -1003,8 +1043,14 @@ def main():
 
     aircraft = AIRCRAFT5 if args.mission == "mixed" else (args.aircraft,)
     keep = {}        # the headline's batch and buffers: re-used by a stated config of the same workload (one GPU: configs[4] fp64)
+    outputs = {} if args.dump_outputs else None
     r = sharded_run(tol_amd, job, args.mission, aircraft, args.ts, args.dtype, args.pattern,
-                    0 if args.global_batch > 0 else args.batch, args.global_batch, args.steps, args.warmup, args.x_buffers, keep=keep)
+                    0 if args.global_batch > 0 else args.batch, args.global_batch, args.steps, args.warmup, args.x_buffers,
+                    instrumented=args.full, keep=keep, outputs=outputs)
+    if outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
     # where every rank's output buffer landed (the placement search of its G buffer): onto its identity card
     placements = [r["placement"]]
     if coll:
@@ -1028,6 +1074,7 @@ def main():
         value = total * args.ts * args.steps / r["elapsed"]
         alg_bytes = r["alg_bytes"]
         achieved = alg_bytes / (r["kern_ms"] * 1e-3) / 1e9
+        fill = r["box_fill_GBs"] if CALIBRATE else None                  # not measured: null in the line, not NaN
         traffic, traffic_source = None, None
         tpath = os.path.join(ROOT, "profiles", "traffic_latest.json")
         if os.path.exists(tpath):
@@ -1062,7 +1109,7 @@ def main():
                        "parallelism": (f"batch-sharded x{world}, {backend} all-gather of objectives") if world > 1 else "single GPU"},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
-                         "box_fill_GBs": r["box_fill_GBs"], "frac_of_box_fill": achieved / r["box_fill_GBs"],
+                         "box_fill_GBs": fill, "frac_of_box_fill": achieved / fill if fill else None,
                          "box_stream_shape_GBs": r.get("box_stream_shape_GBs"), "box_stream_shape_us": r.get("box_stream_shape_us"),
                          "vs_bare_store_loop": achieved / r["box_stream_shape_GBs"] if r.get("box_stream_shape_GBs") else None,
                          "calibration": "reference points, not ceilings, measured in this process on this box right after the timed region: "
@@ -1077,7 +1124,10 @@ def main():
                                    "itself is no slower than this. instrumented_*: a second pass with start/stop events attached "
                                    "to every dispatch, as rocprofv3 --kernel-trace does; dispatch profiling itself lengthens every "
                                    "launch (profiles/r02_event_cost.md)",
-                         "instrumented_kernel_ms": r["inst_ms"], "instrumented_kernel_min_ms": r["inst_min_ms"], "instrumented_ms_per_step": r["inst_step_ms"],
+                         # the instrumented pass runs under --full only
+                         "instrumented_kernel_ms": r["inst_ms"] if args.full else None,
+                         "instrumented_kernel_min_ms": r["inst_min_ms"] if args.full else None,
+                         "instrumented_ms_per_step": r["inst_step_ms"] if args.full else None,
                          "algorithmic_bytes_per_launch": alg_bytes,
                          "bytes_per_node": alg_bytes / max(B * args.ts, 1)},
         }

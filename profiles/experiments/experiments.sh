@@ -101,7 +101,7 @@ r02ai)
 # what attaching start/stop events to every dispatch costs: bench.py reports the uninstrumented timed region and the instrumented pass
 O=gpurun_out/r02ai; mkdir -p $O
 for a in "--batch 4096" "--batch 4096" "--batch 1024 --steps 500" "--batch 128 --steps 2000" "--batch 4096 --ts 2000 --aircraft skywalker --batch 400" "--batch 8192 --mission mixed" "--batch 4096 --dtype f32"; do
-  timeout -k 10 200 python bench.py --no-configs --no-cpu-baseline $a > $O/b.json 2>/dev/null
+  timeout -k 10 200 python bench.py --full --no-configs --no-cpu-baseline $a > $O/b.json 2>/dev/null
   echo "bench.py $a"; python - <<PY
 import json
 d=json.loads(open("$O/b.json").read().strip().splitlines()[-1]); r=d["roofline"]
@@ -310,7 +310,7 @@ O=gpurun_out/r02g
 timeout -k 10 600 python -m pytest tests -m gpu -x -q -s > $O/pytest_gpu.log 2>&1; echo "pytest exit $?"; tail -12 $O/pytest_gpu.log | cut -c1-400
 grep "worst scaled error per class" $O/pytest_gpu.log | cut -c1-1200
 echo "== callback (default)"; timeout -k 10 120 python tools/callback_tool.py rate 2>&1 | tail -5
-timeout -k 10 500 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench exit $?"; tail -3 $O/bench.err; python - <<'PY'
+timeout -k 10 500 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench exit $?"; tail -3 $O/bench.err; python - <<'PY'
 import json
 d=json.loads(open('gpurun_out/r02g/bench.json').read().strip().splitlines()[-1])
 print({k:d[k] for k in ('value','ms_per_step','backend','scaling')}, d['roofline']['frac'], d['roofline']['kernel_ms'])
@@ -341,7 +341,7 @@ mkdir -p gpurun_out/r02i
 O=gpurun_out/r02i
 timeout -k 10 600 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; echo "pytest exit $?"; tail -4 $O/pytest_gpu.log | cut -c1-400
 echo "== callback"; timeout -k 10 120 python tools/callback_tool.py rate 2>&1 | tail -5
-timeout -k 10 500 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench exit $?"; tail -2 $O/bench.err
+timeout -k 10 500 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench exit $?"; tail -2 $O/bench.err
 python tools/show_bench.py $O/bench.json
 timeout -k 10 600 bash tools/profile_gpu.sh r02 > $O/profile.log 2>&1; echo "profile exit $?"; tail -3 $O/profile.log
 timeout -k 10 200 bash tools/pmc_pass.sh ta "TA_ADDR_STALLED_BY_TC_CYCLES_sum TA_DATA_STALLED_BY_TC_CYCLES_sum TA_FLAT_WRITE_WAVEFRONTS_sum" > $O/pmc_ta.txt 2>&1; echo "ta pass exit $?"; cat $O/pmc_ta.txt | tail -6
@@ -477,7 +477,7 @@ r02t)
 mkdir -p gpurun_out/r02t
 O=gpurun_out/r02t
 timeout -k 10 600 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; echo "pytest exit $?"; tail -3 $O/pytest_gpu.log
-timeout -k 10 300 python bench.py --steps 100 --no-cpu-baseline > $O/bench.json 2> $O/bench.err; echo "bench exit $?"; python tools/show_bench.py $O/bench.json
+timeout -k 10 300 python bench.py --full --steps 100 --no-cpu-baseline > $O/bench.json 2> $O/bench.err; echo "bench exit $?"; python tools/show_bench.py $O/bench.json
 ;;
 r02u)
 # round-2 experiment U: own fp32 sin/cos -- GPU suite, fp32 timings against the library routine (same box)
@@ -648,7 +648,7 @@ timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; 
 r03h)
 # the restructured bench.py: default 1-GPU line, then the 2-rank gloo rehearsal on one GPU
 O=gpurun_out/r03h; mkdir -p $O
-timeout -k 10 500 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench exit $?"; tail -3 $O/bench.err; python tools/show_bench.py $O/bench.json
+timeout -k 10 500 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench exit $?"; tail -3 $O/bench.err; python tools/show_bench.py $O/bench.json
 bash tools/rehearse_ranks.sh > $O/rehearse.log 2>&1; echo "rehearse exit $?"; cat $O/rehearse.log | cut -c1-330
 ;;
 r03l)
@@ -741,7 +741,7 @@ timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; 
 TOLFG_NO_SINGLE_LAUNCH=1 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/pytest_gpu_tiled_callback.log 2>&1; echo "pytest (callback through the tile-per-workgroup path) exit $?"; tail -2 $O/pytest_gpu_tiled_callback.log
 TOLFG_FUSED=0 timeout -k 10 900 python -m pytest tests -m gpu -x -q > $O/pytest_gpu_two_launch.log 2>&1; echo "pytest (two-launch form) exit $?"; tail -2 $O/pytest_gpu_two_launch.log
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke exit $?"; tail -1 $O/smoke.log
-timeout -k 10 500 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench exit $?"; python tools/show_bench.py $O/bench.json
+timeout -k 10 500 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench exit $?"; python tools/show_bench.py $O/bench.json
 timeout -k 10 600 bash tools/shape_sweep.sh > $O/shape_sweep.md 2>&1; echo "shape sweep exit $?"; cat $O/shape_sweep.md
 ;;
 r03r)

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,7 +27,7 @@ def test_without_a_gpu_the_ranks_fail_and_the_exit_code_is_relayed():
 def test_plain_command_with_two_ranks_prints_one_line(tmp_path):
     """Two ranks share this box's one GPU over gloo (the rehearsal backend; RCCL needs a GPU per rank)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "5"],
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "5", "--full"],
                          capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
@@ -59,7 +60,7 @@ def test_the_rccl_calls_of_the_multi_rank_path_run_with_one_rank():
     of the buffer the finalizing waves write.  bench.py --single-rank-collectives; the stated configs run sharded as well."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--single-rank-collectives", "--steps", "5", "--warmup", "2",
-                          "--batch", "2048", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                          "--batch", "2048", "--full", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -85,6 +86,42 @@ def test_the_rccl_calls_of_the_multi_rank_path_run_with_one_rank():
     assert 0.5 < nm["ms_per_step"] / line["ms_per_step"] < 2.0
     assert nm["objectives_stored_to_host_instead"]["ms_per_step"] > 0
     assert sorted((r["config"], r["dtype"]) for r in nm["configs"]) == [(3, "f64"), (4, "f32"), (4, "f64")]
+
+
+@pytest.mark.gpu
+def test_a_plain_run_times_the_headline_only_and_dumps_the_last_steps_outputs(tmp_path):
+    """Without --full: exactly --steps timed steps, no side measurements; --dump-outputs writes what the last timed step computed,
+    the same in two runs with the same arguments."""
+    def run(out):
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--batch", "64",
+                              "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+        lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        return json.loads(lines[0]), {n: np.load(out / f"{n}.npy") for n in ("objectives", "F", "G")}
+    line, got = run(tmp_path / "a")
+    assert line["steps"] == 7 and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "node-evals/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f64" and line["config"]["batch_per_gpu"] == 64
+    assert not {"configs", "cpu_baseline", "native_multi", "callback", "s10_batch_4096"} & set(line)
+    assert line["roofline"]["box_fill_GBs"] is None and line["roofline"]["instrumented_kernel_ms"] is None
+    obj, F, G = got["objectives"], got["F"], got["G"]
+    assert obj.dtype == F.dtype == G.dtype == np.float64
+    assert obj.shape == (64,) and F.shape[0] == 64 and G.shape[0] == 64            # small enough to be written whole
+    assert np.isfinite(obj).all() and np.array_equal(obj, F[:, 0]) and np.abs(G).max() > 0
+    _, again = run(tmp_path / "b")
+    for n in got:
+        assert np.array_equal(got[n], again[n], equal_nan=True), n
+
+
+def test_output_sample_is_the_whole_array_or_a_fixed_seeded_sample():
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    a = torch.arange(60, dtype=torch.float64).reshape(6, 10)
+    assert np.array_equal(bench.output_sample(torch, a, 5, 8, 8 * 40, 0), a[:5, :8].numpy())
+    s = bench.output_sample(torch, a, 5, 8, 8 * 10, 1)
+    assert 0 < s.size <= 10 and np.array_equal(s, bench.output_sample(torch, a, 5, 8, 8 * 10, 1))
+    assert set(s.tolist()) <= set(a[:5, :8].reshape(-1).tolist()) and np.all(np.diff(s) > 0)
 
 
 def test_a_process_group_of_another_size_than_gpus_is_refused():

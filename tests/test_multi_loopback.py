@@ -51,7 +51,7 @@ def test_an_explicit_collective_library_that_cannot_be_loaded_is_an_error_not_a_
     assert out.returncode == 0 and "ERR" in out.stdout, out.stdout + out.stderr
     import torch
     if torch.cuda.is_available():
-        assert "TOLFG_RCCL_LIBRARY" in out.stdout and "cannot be loaded" in out.stdout
+        assert "named in the environment" in out.stdout and env["TOLFG_RCCL_LIBRARY"] in out.stdout and "cannot be loaded" in out.stdout
 
 
 def run_worker(tmp_path, mission, dtype, total, parts, N, wind):

@@ -10,6 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 DATA = os.path.join(ROOT, "tol_amd", "data")
 REFSO = os.path.join(ROOT, "oracle", "_ref", "libref_params.so")
+REF_DATA = os.path.join(HERE, "golden", "reference_params")      # the reference's own .param files, as it ships them
 AIRCRAFT = ["tempest", "skywalker", "tempest_eric", "tempest_wences", "tempest_will"]
 
 NASTY = "\n".join([
@@ -82,12 +83,10 @@ def test_wrong_count_is_a_length_error(tmp_path, tolfg):
 
 
 @pytest.mark.skipif(not os.path.exists(REFSO), reason="oracle/_ref not built (needs /root/reference: build container only)")
-@pytest.mark.parametrize("root", [DATA, "/root/reference"])
+@pytest.mark.parametrize("root", [DATA, REF_DATA], ids=["shipped", "reference"])
 def test_against_the_reference_reader(oracle, root):
     """The reference's own reader (compiled in place from src/parameters.cpp) on this repo's data
-    files and, in the build container, on the reference's files: same values as the oracle reads."""
-    if not os.path.isdir(os.path.join(root, "aircraft")):
-        pytest.skip(f"{root} absent")
+    files and on the reference's files (tests/golden/reference_params): same values as the oracle reads."""
     R = C.CDLL(REFSO)
     dp = C.POINTER(C.c_double)
     for fn in (R.ref_aircraft, R.ref_gain, R.ref_limit, R.ref_snopt):

@@ -2,8 +2,8 @@
 # The round's full GPU pass, in parts that each fit one gpurun call (<= 20 min):  tools/gpu_run_all.sh <tag> suites | bench | profile
 #   suites   GPU suite against the shipped library, then against the measurement build (tol_amd/csrc/knobs.h): default plan, the
 #            callback through the one-workgroup kernel, the two-launch form; smoke
-#   bench    bench.py as the driver starts it, at its own defaults, as `--gpus 2` plain command (two ranks on this box's one GPU, gloo),
-#            and as ONE RCCL rank (--single-rank-collectives): every line carries the native C++ leg (native_multi)
+#   bench    bench.py as the driver starts it (the headline alone); with --full at its own defaults, as `--gpus 2` plain command (two
+#            ranks on this box's one GPU, gloo), and as ONE RCCL rank (--single-rank-collectives): each --full line carries the native C++ leg
 #   profile  rocprofv3 --kernel-trace --stats + PMC passes (tools/profile_gpu.sh; then tools/parse_rocprof.py <tag> 8192 200 f64 mixed), shape sweep
 # Raw output under gpurun_out/<tag>/.
 TAG=${1:-r05}
@@ -21,9 +21,9 @@ timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.
 ;;
 bench)
 timeout -k 10 500 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err; echo "bench (the driver's command) exit $?"; python tools/show_bench.py $O/bench_driver_cmd.json
-timeout -k 10 500 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench exit $?"; python tools/show_bench.py $O/bench.json
-timeout -k 10 600 python3 bench.py --gpus 2 --backend gloo --steps 20 --warmup 5 > $O/bench_2ranks_gloo.json 2> $O/bench_2ranks_gloo.err; echo "bench --gpus 2 (plain command, gloo rehearsal) exit $?"; python tools/show_bench.py $O/bench_2ranks_gloo.json | cut -c1-400
-timeout -k 10 600 python3 bench.py --gpus 1 --single-rank-collectives --steps 20 --warmup 5 > $O/bench_1rank_rccl.json 2> $O/bench_1rank_rccl.err; echo "bench, one RCCL rank exit $?"; python tools/show_bench.py $O/bench_1rank_rccl.json | cut -c1-400
+timeout -k 10 500 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench exit $?"; python tools/show_bench.py $O/bench.json
+timeout -k 10 600 python3 bench.py --gpus 2 --backend gloo --steps 20 --warmup 5 --full > $O/bench_2ranks_gloo.json 2> $O/bench_2ranks_gloo.err; echo "bench --gpus 2 (plain command, gloo rehearsal) exit $?"; python tools/show_bench.py $O/bench_2ranks_gloo.json | cut -c1-400
+timeout -k 10 600 python3 bench.py --gpus 1 --single-rank-collectives --steps 20 --warmup 5 --full > $O/bench_1rank_rccl.json 2> $O/bench_1rank_rccl.err; echo "bench, one RCCL rank exit $?"; python tools/show_bench.py $O/bench_1rank_rccl.json | cut -c1-400
 ;;
 profile)
 timeout -k 10 600 bash tools/profile_gpu.sh $TAG > $O/profile.log 2>&1; echo "profile exit $?"; tail -2 $O/profile.log      # then: python tools/parse_rocprof.py $TAG 8192 200 f64 mixed

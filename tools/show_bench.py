@@ -9,8 +9,8 @@ r = d["roofline"]
 nan = float("nan")
 print("value %.4g %s on %d GPU(s), %s scaling, backend %s; ms/step %.4f; per launch %.4f ms -> %.0f GB/s = %.3f of peak  (instrumented pass: %.4f ms, min %.4f)"
       % (d["value"], d["unit"], d["n_gpus"], d["scaling"], d.get("backend"), d["ms_per_step"], r["kernel_ms"], r["achieved"], r["frac"],
-         r.get("instrumented_kernel_ms", nan), r.get("instrumented_kernel_min_ms", r.get("kernel_min_ms", nan))))
-if "box_fill_GBs" in r:
+         r.get("instrumented_kernel_ms") or nan, r.get("instrumented_kernel_min_ms") or r.get("kernel_min_ms") or nan))
+if r.get("box_fill_GBs"):      # the calibration runs under --full only
     print("  this box, same process: vendor fill %.0f GB/s (the launch = %.3f of it); bare store loop of the launch's shape %.1f us = %.0f GB/s over its slab bytes; warm-up %s steps"
           % (r["box_fill_GBs"] or nan, r.get("frac_of_box_fill") or nan, r.get("box_stream_shape_us") or nan, r.get("box_stream_shape_GBs") or nan, d.get("warmup_steps_run")))
 for c in d.get("configs", []):
